@@ -7,7 +7,9 @@ low-res-shaped columns gathered by a random permutation from an HBM-resident spl
 gather+normalise-cast -> 7 Dense forward -> fused MSE/dz -> 7 wgrad + 6 dgrad -> (N>1: ONE RCCL
 all-reduce of the flat fp32 gradient) -> fused optimiser + bf16 re-cast.  Nothing is skipped.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch PER_GPU_BATCH]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch PER_GPU_BATCH] [--dump-outputs DIR]
+  The timed region is exactly K steps after W untimed ones (`--min-seconds S` repeats the K-step block until S seconds are timed);
+  `ms_per_step` in the line is what one timed step took.  --dump-outputs writes what the last timed step computed (dump_outputs).
   N>1: one rank per GPU.  Either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`
   (RANK / LOCAL_RANK / WORLD_SIZE in the environment) or plainly as `python bench.py --gpus N`: the parent then touches no
   GPU and starts the N ranks itself as a child process group (torch.distributed.run on 127.0.0.1), passing stdout through.
@@ -714,6 +716,23 @@ def block_stats(secs, steps, cols_per_step):
                               "worst": round(cols_per_step * steps / s[-1], 1)}}, med
 
 
+def dump_outputs(out_dir, model, loss):
+    """What the timed path hands its caller after its last step, as `out_dir/<name>.npy` (float32, ~14 MB for the cfg-MLP):
+    `loss` = that step's [sum of squared errors, sum of absolute errors] over its batch (the device tensor train_on_batch returns),
+    `weight_NN` = the model's arrays in Keras order (kernel (in, out), bias, ...), `adam_m_NN` / `adam_v_NN` = the optimiser's
+    moments in the same order.  Data, initial weights and batch order are seeded, so two builds run with the same arguments can
+    be compared array for array.  Returns the names written."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": loss.detach().cpu().numpy()}
+    arrays.update({"weight_%02d" % i: w for i, w in enumerate(model.get_weights())})
+    m, v, _ = model.get_optimizer_state()
+    arrays.update({"adam_m_%02d" % i: a for i, a in enumerate(m)})
+    arrays.update({"adam_v_%02d" % i: a for i, a in enumerate(v)})
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    return sorted(arrays)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -721,7 +740,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--batch", type=int, default=8192, help="per-GPU batch (columns per rank per step)")
     ap.add_argument("--rows", type=int, default=1 << 20, help="HBM-resident synthetic rows per GPU")
-    ap.add_argument("--min-seconds", type=float, default=1.0, help="repeat the --steps block until this much step time is measured")
+    ap.add_argument("--min-seconds", type=float, default=0.0, help="repeat the --steps block until this much step time is measured "
+                    "(default 0: one block, so that the timed region is exactly --steps steps)")
     ap.add_argument("--strong-global-batch", type=int, default=8192, help="N>1: global batch of the strong-scaling leg (BASELINE configs[3]); 0 = skip")
     ap.add_argument("--weak-large-batch", type=int, default=65536, help="N>1: per-GPU batch of a second weak-scaling leg (0 = skip)")
     ap.add_argument("--grad-payload", choices=("fp32", "bf16"), default="fp32", help="N>1: what the gradient all-reduce sends (fp32 = the reference's DDP; "
@@ -736,6 +756,8 @@ def main():
     ap.add_argument("--extras", default="pub_mlp,cnn,loader,stream,sweep", help="which side figures to take (comma-separated)")
     ap.add_argument("--train-only", action="store_true", help="counter runs: nothing but the training steps (no held-out "
                     "evaluation, no prediction pass), so that per-kernel averages are averages over training launches")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed "
+                    "(its loss sums, the model's weights and Adam moments) to DIR/<name>.npy, float32 (see dump_outputs)")
     args = ap.parse_args()
 
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")     # dmabuf IPC: what RCCL needs between the ranks of this pool's hosts
@@ -863,6 +885,8 @@ def run(args, world, rank):
     timing, med = block_stats(secs, args.steps, B * world)
     ms_per_step = med / args.steps * 1e3                            # the median block: EXACTLY --steps steps between barriers
     value = B * world * args.steps / med
+    if args.dump_outputs and rank == 0:                             # before any other leg touches the model
+        dump_outputs(args.dump_outputs, model, loss)
     held = None if args.train_only else model.evaluate(xv, yv)      # the model the timed region trained, before any other leg touches it
     per_var = None
     if rank == 0 and not args.train_only:

@@ -73,6 +73,43 @@ def test_bench_defaults_and_flags():
     assert 'default=1)' in src.split('"--gpus"')[1][:60]            # no flags: one GPU
 
 
+def test_steps_set_the_timed_region_and_outputs_are_dumped_by_name(tmp_path):
+    """--steps K without --min-seconds: timed_blocks runs ONE block of exactly K steps, numbered on from the warm-up.
+    --dump-outputs DIR: bench.dump_outputs writes the loss pair, the weights and both Adam moments, one float32 .npy per array.
+    Both driven here with stand-ins for torch and the model (no GPU)."""
+    import importlib
+    import sys
+    import types
+
+    import numpy as np
+    import torch
+    sys.path.insert(0, REPO)
+    bench = importlib.import_module("bench")
+    assert "default=0.0" in open(os.path.join(REPO, "bench.py")).read().split('"--min-seconds"')[1][:30]
+    seen = []
+    stub = types.SimpleNamespace(cuda=types.SimpleNamespace(synchronize=lambda: None))
+    secs = bench.timed_blocks(stub, None, None, seen.append, 7, 3, 0.0)
+    assert len(secs) == 1 and seen == list(range(3, 10))
+
+    ws = [np.arange(6, dtype=np.float64).reshape(2, 3), np.full(3, 0.5, np.float32)]
+
+    class Model:
+        def get_weights(self):
+            return ws
+
+        def get_optimizer_state(self):
+            return [w * 2 for w in ws], [w * 3 for w in ws], 7
+
+    out = tmp_path / "out"
+    names = bench.dump_outputs(str(out), Model(), torch.tensor([1.5, 2.5]))
+    assert names == ["adam_m_00", "adam_m_01", "adam_v_00", "adam_v_01", "loss", "weight_00", "weight_01"]
+    assert sorted(p.stem for p in out.iterdir()) == names
+    got = {n: np.load(out / f"{n}.npy") for n in names}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert np.array_equal(got["loss"], [1.5, 2.5]) and np.array_equal(got["weight_00"], ws[0]) and got["weight_00"].shape == (2, 3)
+    assert np.array_equal(got["adam_m_01"], ws[1] * 2) and np.array_equal(got["adam_v_00"], ws[0] * 3)
+
+
 def test_bench_gpus_n_starts_its_own_ranks():
     """`python bench.py --gpus 2` without a launcher (the driver's command shape): the parent must start two ranks itself
     instead of exiting.  Without a GPU here every rank stops at the "needs a GPU" check - which proves the children ran

@@ -77,6 +77,29 @@ def test_one_gpu_line_with_the_cpu_legs():
     assert d["cpu_baseline"]["value"] > 0
 
 
+def test_dump_outputs_of_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: without --min-seconds the timed region is one block of exactly --steps steps, and what its last step
+    computed (loss sums, weights and Adam moments in Keras order, float32, at most 64 MB) lands under DIR.  The inputs are seeded:
+    a second run with the same arguments computes the same arrays."""
+    import numpy as np
+    args = ["--steps", "5", "--warmup", "2", "--rows", "65536", "--cpu-budget", "0", "--no-extras", "--no-profile"]
+    dumps = []
+    for k in range(2):
+        out = tmp_path / f"run{k}"
+        d = run([*args, "--dump-outputs", str(out)])
+        assert d["steps"] == 5 and d["timing"]["blocks"] == 1 and d["timing"]["steps_per_block"] == 5 and d["ms_per_step"] > 0
+        files = sorted(out.glob("*.npy"))
+        assert sum(f.stat().st_size for f in files) <= 64 << 20
+        dumps.append({f.stem: np.load(f) for f in files})
+    a, b = dumps
+    assert sorted(a) == sorted(b) and len(a) == 1 + 3 * 16
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values())
+    assert a["loss"].shape == (2,) and (a["loss"] > 0).all()
+    assert a["weight_00"].shape == (124, 512) and a["weight_15"].shape == (8,) and (a["adam_v_00"] > 0).any()
+    for name in a:
+        np.testing.assert_allclose(a[name], b[name], rtol=1e-5, atol=1e-9, err_msg=name)
+
+
 def test_two_ranks_start_themselves_and_report_weak_strong_and_comm():
     d = run(["--gpus", "2", *FAST, "--no-profile", "--batch", "2048", "--weak-large-batch", "8192", "--time-oneshot"], {"CS_BENCH_SHARE_GPU": "1"})
     assert d["n_gpus"] == 2 and d["config"]["parallelism"] == "dp2" and d["config"]["global_batch"] == 4096
