@@ -293,3 +293,61 @@ def synth_columns(n, seed=20230614, n_in=124, n_out=128):
     y[:, 120:] = np.maximum(y[:, 120:], 0)
     y[:, 60:72] = 0
     return x, y
+
+
+# ------------------------------------------------------------------------------- sums by rows
+@dataclass
+class RowSums:
+    """What the engine returns for a set of rows, UNSCALED: `sq` / `ab` = the loss sums (squared / absolute error over rows and
+    the 128 outputs; cs_mlp_loss_grads' two floats), `grads` = Keras-ordered float64 gradients of `sq` (get_gradients(1.0)),
+    `row_sq` = each row's squared error and `yhat` each row's prediction, in row order.  The `bf16=True` rounding points are per element, so the sums over rows
+    [0, n) are the sums of any row blocks that cover them: `a + b` is the result of the rows of `a` followed by those of `b`."""
+    sq: float
+    ab: float
+    grads: list
+    row_sq: np.ndarray
+    yhat: np.ndarray
+
+    def __add__(self, o: "RowSums") -> "RowSums":
+        return RowSums(self.sq + o.sq, self.ab + o.ab, [a + b for a, b in zip(self.grads, o.grads)],
+                       np.concatenate([self.row_sq, o.row_sq]), np.concatenate([self.yhat, o.yhat]))
+
+    def mean_grads(self):
+        """The gradients of the mean squared error (what loss_and_grads returns), float32."""
+        s = 1.0 / (128.0 * len(self.row_sq))
+        return [(g * s).astype(F32) for g in self.grads]
+
+
+def row_sums(ws, x, y, cfg: MLPConfig, bf16=True) -> RowSums:
+    """RowSums of the rows of (x, y): one loss_and_grads call rescaled by n_out * rows."""
+    x, y = np.asarray(x, F32), np.asarray(y, F32)
+    b = x.shape[0]
+    if b == 0:
+        return RowSums(0.0, 0.0, [np.zeros(w.shape, np.float64) for w in ws], np.zeros(0), np.zeros((0, cfg.n_out), F32))
+    loss, mae, grads, yhat = loss_and_grads(ws, x, y, cfg, bf16=bf16)
+    s = float(cfg.n_out * b)
+    row_sq = ((yhat - y).astype(np.float64) ** 2).sum(axis=1)                # (float32 error, as loss_and_grads)
+    return RowSums(loss * s, mae * s, [g.astype(np.float64) * s for g in grads], row_sq, yhat)
+
+
+class RowBlockOracle:
+    """RowSums of the leading rows of one data set under one set of weights, from cached blocks: rows [0, n) are the aligned
+    `block`-row blocks below n plus one short block, so n and n +- 1 cost one small extra block, not a second full pass."""
+
+    def __init__(self, ws, x, y, cfg: MLPConfig, block=1024, bf16=True):
+        self.ws, self.x, self.y, self.cfg, self.block, self.bf16 = ws, x, y, cfg, int(block), bf16
+        self._cache = {}
+
+    def _block(self, lo, hi) -> RowSums:
+        if (lo, hi) not in self._cache:
+            self._cache[(lo, hi)] = row_sums(self.ws, self.x[lo:hi], self.y[lo:hi], self.cfg, bf16=self.bf16)
+        return self._cache[(lo, hi)]
+
+    def leading(self, n) -> RowSums:
+        if n > self.x.shape[0]:
+            raise ValueError(f"{n} rows asked of a data set of {self.x.shape[0]}")
+        full = (n // self.block) * self.block
+        out = row_sums(self.ws, self.x[:0], self.y[:0], self.cfg)
+        for lo in range(0, full, self.block):
+            out = out + self._block(lo, lo + self.block)
+        return out + self._block(full, n) if n > full else out

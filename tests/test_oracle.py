@@ -261,3 +261,28 @@ def test_cnn_loss_functions_match_the_reference_function_bodies():
         assert abs(CO.mae_adjusted(yt, yp) - float(gold[f"{key}/mae_adjusted"])) <= 1e-12
         assert abs(CO.mse_adjusted(yt, yp) - float(gold[f"{key}/mse_adjusted"])) <= 1e-12
         assert abs(CO.continuous_ranked_probability_score(yt, yp) - float(gold[f"{key}/continuous_ranked_probability_score"])) <= 1e-12
+
+
+@pytest.mark.parametrize("n", [1, 1023, 1024, 1025, 2500])
+def test_row_block_sums_equal_one_call(n):
+    """RowBlockOracle (aligned blocks + one short block, cached) against ONE loss_and_grads call over the same rows rescaled by
+    128 n: the bf16 rounding points are per element, so the two differ by float64 summation order and the float32 rounding of
+    each call's outputs."""
+    cfg = O.MLPConfig(hidden=(512, 512, 256))
+    ws = O.glorot_init(cfg, 2)
+    x, y = O.synth_columns(2600, seed=5)
+    blocks = O.RowBlockOracle(ws, x, y, cfg, block=512)
+    got = blocks.leading(n)
+    loss, mae, grads, yhat = O.loss_and_grads(ws, x[:n], y[:n], cfg, bf16=True)
+    assert got.sq == pytest.approx(loss * 128 * n, rel=1e-12)
+    assert got.ab == pytest.approx(mae * 128 * n, rel=1e-12)
+    for g, r in zip(got.grads, grads):
+        d = np.linalg.norm(g - r.astype(np.float64) * (128 * n)) / (np.linalg.norm(r) * 128 * n + 1e-30)
+        assert d <= 1e-6, d
+    np.testing.assert_array_equal(got.yhat, yhat)
+    assert got.row_sq.shape == (n,)
+    assert got.row_sq.sum() == pytest.approx(got.sq, rel=1e-12)
+    # the blocks are cached: n + 1 after n reuses every aligned block
+    cached = len(blocks._cache)
+    blocks.leading(n + 1)
+    assert len(blocks._cache) <= cached + 1
