@@ -18,6 +18,7 @@ CS_FLAG_CHAIN_BWD32_ON_FWD64 = 32
 CS_FLAG_GEMM_V1 = 64
 CS_FLAG_NO_CHAIN_FB = 256
 CS_FLAG_COOP = 512
+CS_FLAG_FP32 = 1024               # float32 arithmetic on f32-input MFMA (csrc/gemm_f32.h); include/climsim_hip.h
 
 ACT = {"relu": 0, "elu": 1, "leakyrelu": 2}
 OPT = {"Adam": 0, "RAdam": 1, "RMSprop": 2, "SGD": 3, "AdamTorch": 4}

@@ -11,6 +11,7 @@
 #include "chainw.h"
 #include "coop.h"
 #include "metrics.h"
+#include "gemm_f32.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -106,6 +107,7 @@ struct Layer {
     int bias_off = 0;                   // offset of the bias in the chain kernels' LDS bias block
     u16 *H;                    // layer INPUT activations [m_pad_max][Kp]
     u16 *dZ;                   // d loss / d pre-activation of this layer [m_pad_max][N]
+    float *Hf = nullptr, *dZf = nullptr;   // CS_FLAG_FP32: the same two in float32 (H and dZ are then not allocated)
 };
 
 }  // namespace
@@ -139,6 +141,7 @@ struct cs_mlp {
     int64_t bytes = 0;
     int n_cu = 0;                  // compute units of the device (hipDeviceProp_t::multiProcessorCount)
     bool use_chain = false;
+    bool fp32 = false;         // CS_FLAG_FP32: float32 operands on the per-layer path (gemm_f32.h)
     bool bwd_chain_done = false;   // run_forward launched k_chain_fb: run_backward goes straight to the weight gradients
     bool chainw_stream = true; // wide chain: continuous weight stream (cws_tile, chainw.h); CS_CHAINW_STREAM=0 = the per-pass form
     bool use_chainw = false;   // wide-model chain (chainw.h): widths any multiple of 128 up to 1024, batches up to chainw_max_n
@@ -439,8 +442,106 @@ void chain_fwd_args(const cs_mlp* h, bool wide, const float* x, const int64_t* r
     }
 }
 
+// ---- float32 arithmetic mode (CS_FLAG_FP32, gemm_f32.h): the per-layer path on float32 buffers, weights read from P
+// 128 x 128 tiles where they alone put a workgroup on every CU, else 64 x 64 (the published widths at 3072 columns: 144 tiles of
+// 128 x 128 per layer against 576 of 64 x 64 - f32 MFMA is 1/16 of the bf16 rate, so these GEMMs are compute-bound and idle CUs
+// cost their share in full).
+template <int EPI, bool WT>
+void launch_gemm_f32(const cs_mlp* h, int64_t m_pad, const GemmF32& p, hipStream_t st) {
+    const int ncu = h->n_cu > 0 ? h->n_cu : 256;
+    if ((m_pad / 128) * (p.N / 128) >= ncu)
+        CS_LAUNCH((k_gemm_f32<EPI, WT, 128, 128>), dim3((unsigned)(m_pad / 128), (unsigned)(p.N / 128)), dim3(256), 0, st, p);
+    else
+        CS_LAUNCH((k_gemm_f32<EPI, WT, 64, 64>), dim3((unsigned)(m_pad / 64), (unsigned)(p.N / 64)), dim3(256), 0, st, p);
+}
+
+int run_forward_f32(cs_mlp* h, const float* x, const int64_t* row_idx, int64_t n, int normalise, float* yhat,
+                    const float* y, float* loss, bool want_dz, hipStream_t st) {
+    const int64_t m_pad = round_up(n, 128);
+    const Layer& l0 = h->layers[0];
+    {
+        const int64_t total = m_pad * (l0.Kp / 4);
+        ProfScope ps(CS_K_PREPARE, st);
+        CS_LAUNCH(k_prepare_input_f32, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, x, row_idx, n,
+                  m_pad, h->cfg.n_in, l0.Kp, h->sub, h->div, normalise, l0.Hf);
+    }
+    for (int l = 0; l < h->L; ++l) {
+        const Layer& ly = h->layers[l];
+        GemmF32 p{};
+        p.A = ly.Hf; p.lda = ly.Kp; p.W = h->P + ly.w_off; p.ldw = ly.N; p.w_rows = ly.K; p.K = ly.K; p.N = ly.N;
+        p.act = h->cfg.act; p.alpha = (h->cfg.act == CS_ACT_RELU) ? 0.f : h->cfg.alpha;
+        p.bias = h->P + ly.b_off;
+        ProfScope ps(CS_K_GEMM_FWD, st);
+        if (l + 1 < h->L) {
+            p.out = h->layers[l + 1].Hf; p.ldo = h->layers[l + 1].Kp;
+            launch_gemm_f32<EPI_HIDDEN, false>(h, m_pad, p, st);
+        } else {
+            p.n_lin = h->cfg.n_out_lin; p.n_real = h->n_out; p.yhat = yhat; p.y = y; p.row_idx = row_idx; p.n_rows = n; p.loss = loss;
+            p.loss_stripes = h->loss_striped ? LOSS_STRIPES : 1; p.loss_kind = h->loss_kind; p.keep = h->keep;
+            p.out = want_dz ? ly.dZf : nullptr; p.ldo = ly.N;
+            launch_gemm_f32<EPI_OUT, false>(h, m_pad, p, st);
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return CS_OK;
+}
+
+// Data gradients layer by layer, then the weight gradients of all layers in one launch.  Inside a training step the row splits
+// STORE their partial sums (split 0 into G, split s into Gx part s - 1) and the optimiser adds them in a fixed order; a
+// cs_mlp_loss_grads call (which may accumulate micro-batches into G) runs one split that adds into G.  No atomics either way:
+// the same data gives the same bits.
+int run_backward_f32(cs_mlp* h, int64_t n, bool accumulate, hipStream_t st) {
+    const int64_t m_pad = round_up(n, 128);
+    for (int l = h->L - 1; l >= 1; --l) {
+        const Layer& ly = h->layers[l];
+        GemmF32 p{};
+        p.A = ly.dZf; p.lda = ly.N; p.W = h->P + ly.w_off; p.ldw = ly.N; p.w_rows = ly.K; p.K = ly.N; p.N = ly.Kp;
+        p.act = h->cfg.act; p.alpha = (h->cfg.act == CS_ACT_RELU) ? 0.f : h->cfg.alpha;
+        p.out = h->layers[l - 1].dZf; p.ldo = h->layers[l - 1].N;
+        p.hprev = ly.Hf; p.ldh = ly.Kp;
+        ProfScope ps(CS_K_GEMM_DGRAD, st);
+        launch_gemm_f32<EPI_DGRAD, true>(h, m_pad, p, st);
+    }
+    const bool plain = h->in_step && !accumulate;
+    const int ncu = h->n_cu > 0 ? h->n_cu : 256;
+    const int slabs = (int)(m_pad / F32_BK);
+    // tile and row splits: fewest rounds of workgroups times the work of one (64 x 64 tiles reuse each operand half as often: x1.3)
+    int bt = 128, splitk = 1;
+    double best = 1e300;
+    for (int t : {128, 64}) {
+        int tiles = 0;
+        for (int l = 0; l < h->L; ++l) tiles += (h->layers[l].Kp / t) * (h->layers[l].N / t);
+        for (int sk = 1; sk <= (plain ? CS_WGRAD_F32_PARTS + 1 : 1) && sk <= slabs; ++sk) {
+            const double rounds = (double)((tiles * sk + ncu - 1) / ncu);
+            const double cost = rounds * (double)t * t * ((slabs + sk - 1) / sk) * (t == 64 ? 1.3 : 1.0);
+            if (cost < best * (1.0 - 1e-9)) { best = cost; bt = t; splitk = sk; }
+        }
+    }
+    WgradF32Args w{};
+    w.n_layers = h->L; w.m_pad = m_pad; w.splitk = splitk; w.accumulate = plain ? 0 : 1;
+    w.g_base = h->G; w.part = h->Gx; w.part_stride = h->n_params;
+    int wg = 0;
+    for (int l = 0; l < h->L; ++l) {
+        const Layer& ly = h->layers[l];
+        WgradF32Layer& d = w.L[l];
+        d.H = ly.Hf; d.ldh = ly.Kp; d.Z = ly.dZf; d.ldz = ly.N;
+        d.dW = h->G + ly.w_off; d.N = ly.N; d.k_real = ly.K; d.db = h->G + ly.b_off;
+        d.tiles_i = ly.Kp / bt; d.tiles_j = ly.N / bt; d.wg_begin = wg;
+        wg += d.tiles_i * d.tiles_j * splitk;
+    }
+    h->gx_parts = plain ? splitk - 1 : 0;
+    h->g_stored = plain;
+    h->g_need_zero = false;
+    ProfScope ps(CS_K_WGRAD, st);
+    if (bt == 128) CS_LAUNCH(k_wgrad_f32<128>, dim3((unsigned)wg), dim3(256), 0, st, w);
+    else CS_LAUNCH(k_wgrad_f32<64>, dim3((unsigned)wg), dim3(256), 0, st, w);
+    HIP_TRY(hipGetLastError());
+    return CS_OK;
+}
+
 int run_forward(cs_mlp* h, const float* x, const int64_t* row_idx, int64_t n, int normalise, float* yhat,
                 const float* y, float* loss, bool want_dz, hipStream_t st) {
+    if (h->fp32) return run_forward_f32(h, x, row_idx, n, normalise, yhat, y, loss, want_dz, st);
     const int64_t m_pad = round_up(n, 128);
     const Layer& l0 = h->layers[0];
     if (h->use_chain) {
@@ -567,6 +668,7 @@ int run_forward(cs_mlp* h, const float* x, const int64_t* row_idx, int64_t n, in
 }
 
 int run_backward(cs_mlp* h, int64_t n, bool atomics_needed, hipStream_t st) {
+    if (h->fp32) return run_backward_f32(h, n, atomics_needed, st);
     const int64_t m_pad = round_up(n, 128);
     const int steps = (int)(m_pad / 64);
     const bool tr = !(h->cfg.flags & CS_FLAG_NO_TR_READ);
@@ -733,6 +835,8 @@ int cs_mlp_create(cs_mlp_t** out, const cs_mlp_cfg* cfg) {
     if (cfg->act < 0 || cfg->act > 2) return fail(CS_ERR_INVALID, "unknown activation %d", cfg->act);
     if (cfg->optimizer < 0 || cfg->optimizer > 4) return fail(CS_ERR_INVALID, "unknown optimizer %d", cfg->optimizer);
     if (cfg->max_batch <= 0) return fail(CS_ERR_INVALID, "max_batch must be positive");
+    if ((cfg->flags & CS_FLAG_FP32) && (cfg->flags & CS_FLAG_COOP))
+        return fail(CS_ERR_INVALID, "CS_FLAG_FP32 runs the per-layer float32 kernels: the cooperative layer chain (CS_FLAG_COOP) is bf16 only");
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (cfg->device < 0 || cfg->device >= ndev) return fail(CS_ERR_INVALID, "device %d not in 0..%d", cfg->device, ndev - 1);
@@ -782,6 +886,8 @@ int cs_mlp_create(cs_mlp_t** out, const cs_mlp_cfg* cfg) {
     }
     if (getenv("CS_FORCE_CHAINW") && atoi(getenv("CS_FORCE_CHAINW"))) h->use_chain = false;   // development: the wide chain on a model the tuned kernels would take
     if (h->use_chain) h->use_chainw = false;               // the tuned kernels take the 128/256/512 models
+    h->fp32 = (cfg->flags & CS_FLAG_FP32) != 0;
+    if (h->fp32) { h->use_chain = false; h->use_chainw = false; }   // float32: the per-layer kernels of gemm_f32.h, whatever the shape
     if (const char* e = getenv("CS_CHAINW_MAX_N")) h->chainw_max_n = atoll(e);
     if (const char* e = getenv("CS_CHAINW_STREAM")) h->chainw_stream = atoi(e) != 0;
     if (h->use_chainw) {
@@ -826,14 +932,14 @@ int cs_mlp_create(cs_mlp_t** out, const cs_mlp_cfg* cfg) {
     A((void**)&h->M, sizeof(float) * off);
     A((void**)&h->V, sizeof(float) * off);
     A((void**)&h->G, sizeof(float) * off);
-    A((void**)&h->Gx, sizeof(float) * off * CS_WGRAD_PARTS);
+    A((void**)&h->Gx, sizeof(float) * off * (h->fp32 ? CS_WGRAD_F32_PARTS : CS_WGRAD_PARTS));
     A((void**)&h->loss_ring, sizeof(float) * 2 * LOSS_STRIPES * LOSS_STRIPE_FLOATS);
     A((void**)&h->keep_store, sizeof(float) * h->n_outp);
     A((void**)&h->sub, sizeof(float) * cfg->n_in);
     A((void**)&h->div, sizeof(float) * cfg->n_in);
     for (int l = 0; l < h->L; ++l) {
         Layer& ly = h->layers[l];
-        if (!h->use_chain) {
+        if (!h->use_chain && !h->fp32) {                      // (float32: the kernels read the master weights P; no operand copies)
             A((void**)&ly.Wt, sizeof(u16) * ly.N * ly.Kp);
             A((void**)&ly.Wn, sizeof(u16) * ly.Kp * ly.N);
         }
@@ -861,6 +967,11 @@ int cs_mlp_create(cs_mlp_t** out, const cs_mlp_cfg* cfg) {
         for (int l = 0; l + 1 < h->L; ++l) A((void**)&h->layers[l].mask, (size_t)(h->m_pad_max / 32) * 512 * 16);
     for (int l = 0; l < h->L; ++l) {       // activations last: the big, streamed part
         Layer& ly = h->layers[l];
+        if (h->fp32) {
+            A((void**)&ly.Hf, sizeof(float) * h->m_pad_max * ly.Kp);
+            A((void**)&ly.dZf, sizeof(float) * h->m_pad_max * ly.N);
+            continue;
+        }
         A((void**)&ly.H, sizeof(u16) * h->m_pad_max * ly.Kp);
         A((void**)&ly.dZ, sizeof(u16) * h->m_pad_max * ly.N);
     }
@@ -944,6 +1055,7 @@ int cs_mlp_set_dropout(cs_mlp_t* h, double rate, uint64_t seed) {
     if (!h) return fail(CS_ERR_INVALID, "null handle");
     if (!(rate >= 0.0 && rate < 1.0)) return fail(CS_ERR_INVALID, "dropout rate %g outside [0, 1)", rate);
     if (rate > 0.0) {
+        if (h->fp32) return fail(CS_ERR_INVALID, "dropout is not built for CS_FLAG_FP32 models (the masks live in the bf16 layer-chain kernels)");
         if (h->cfg.act != CS_ACT_RELU) return fail(CS_ERR_INVALID, "dropout is built for ReLU stacks (Linear -> Dropout -> ReLU, MLP_v2rh/training/mlp.py:41-52)");
         if (h->use_chain) { h->use_chain = false; h->use_chainw = true; }    // the wide chain carries the dropout epilogue
         if (!h->use_chainw) return fail(CS_ERR_INVALID, "dropout needs the wide layer-chain kernels (widths up to 1024, no CS_FLAG_NO_CHAIN)");
@@ -1506,8 +1618,8 @@ extern "C" {
 
 int cs_mlp_kernel_family(const cs_mlp_t* h) {
     if (!h) return -1;
-    const int fam = h->use_chain ? 1 : (h->use_chainw ? 2 : 0);
-    return fam | ((h->cfg.act == CS_ACT_ELU) ? 16 : 0);
+    const int fam = h->use_chain ? 1 : (h->use_chainw ? 2 : 0);     // (0 | 32 for CS_FLAG_FP32: no grouped kernels)
+    return fam | ((h->cfg.act == CS_ACT_ELU) ? 16 : 0) | (h->fp32 ? 32 : 0);
 }
 
 int cs_mlp_group_create(cs_mlp_group_t** out, cs_mlp_t* const* members, int32_t k) {
@@ -1519,6 +1631,8 @@ int cs_mlp_group_create(cs_mlp_group_t** out, cs_mlp_t* const* members, int32_t 
         for (int j = 0; j < i; ++j)
             if (members[j] == members[i]) return fail(CS_ERR_INVALID, "member %d appears twice", i);
     }
+    for (int i = 0; i < k; ++i)
+        if (members[i]->fp32) return fail(CS_ERR_INVALID, "member %d is a CS_FLAG_FP32 model: grouped launches run the bf16 layer-chain kernels only", i);
     const int fam = cs_mlp_kernel_family(members[0]);
     if ((fam & 15) == 0) return fail(CS_ERR_INVALID, "grouped launches need the layer-chain kernels (hidden widths multiples of 128 up to 1024, no CS_FLAG_NO_CHAIN)");
     for (int i = 0; i < k; ++i) {

@@ -113,19 +113,12 @@ __device__ __forceinline__ void loss_flush(float* __restrict__ loss, int stripes
 }
 
 // ---------------------------------------------------------------- input staging
-// h0[m][0..127] = bf16( normalise ? (x-sub)/div with inf/nan->0 : x ), zero for cols >= n_in and
-// rows >= n (rows up to m_pad are written so that later tiles read finite data).
-// One thread = 4 consecutive features.  x rows are n_in floats (124 -> 496 B, 16-B aligned).
-__global__ __launch_bounds__(256) void k_prepare_input(const float* __restrict__ x, const int64_t* __restrict__ row_idx,
-                                                       int64_t n, int64_t m_pad, int n_in, int kp,
-                                                       const float* __restrict__ sub, const float* __restrict__ div,
-                                                       int normalise, u16* __restrict__ h0) {
-    const int groups = kp >> 2;
-    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= m_pad * groups) return;
-    const int64_t m = gid / groups;
-    const int c = (int)(gid - m * groups) * 4;
-    float v[4] = {0.f, 0.f, 0.f, 0.f};
+// Four consecutive features c..c+3 of batch row m: normalise ? (x-sub)/div with inf/nan->0 : x, zero for cols >= n_in and
+// rows >= n.  Shared by k_prepare_input (bf16 H0) and k_prepare_input_f32 (gemm_f32.h, float32 H0).
+__device__ __forceinline__ void prepare4(const float* __restrict__ x, const int64_t* __restrict__ row_idx, int64_t n, int n_in,
+                                         const float* __restrict__ sub, const float* __restrict__ div, int normalise,
+                                         int64_t m, int c, float (&v)[4]) {
+    v[0] = 0.f; v[1] = 0.f; v[2] = 0.f; v[3] = 0.f;
     if (m < n && c < n_in) {
         const int64_t src = row_idx ? row_idx[m] : m;
         const float* xr = x + src * n_in + c;
@@ -144,6 +137,21 @@ __global__ __launch_bounds__(256) void k_prepare_input(const float* __restrict__
                 }
         }
     }
+}
+
+// h0[m][0..127] = bf16(prepare4), rows up to m_pad are written so that later tiles read finite data.
+// One thread = 4 consecutive features.  x rows are n_in floats (124 -> 496 B, 16-B aligned).
+__global__ __launch_bounds__(256) void k_prepare_input(const float* __restrict__ x, const int64_t* __restrict__ row_idx,
+                                                       int64_t n, int64_t m_pad, int n_in, int kp,
+                                                       const float* __restrict__ sub, const float* __restrict__ div,
+                                                       int normalise, u16* __restrict__ h0) {
+    const int groups = kp >> 2;
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= m_pad * groups) return;
+    const int64_t m = gid / groups;
+    const int c = (int)(gid - m * groups) * 4;
+    float v[4];
+    prepare4(x, row_idx, n, n_in, sub, div, normalise, m, c, v);
     *reinterpret_cast<uint2*>(h0 + m * kp + c) = pack4(v[0], v[1], v[2], v[3]);
 }
 

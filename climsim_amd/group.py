@@ -18,7 +18,8 @@ from . import _lib
 
 def kernel_family(model) -> int:
     """1 = tuned layer chain (hidden widths 128/256/512, 128 outputs), 2 = wide layer chain, 0 = one GEMM per layer
-    (cannot be grouped); +16 for ELU.  Members of a group must agree."""
+    (cannot be grouped); +16 for ELU; 32 (+16) for a float32 model (precision="fp32", cannot be grouped).  Members of a group
+    must agree."""
     return int(model.lib.cs_mlp_kernel_family(model._h))
 
 

@@ -82,7 +82,8 @@ class MLPEmulator:
                  output_length_relu: int = 8, alpha: float = 0.15, max_batch: int = 8192,
                  device: Optional[int] = None, seed: Optional[int] = 0, beta_1: float = 0.9,
                  beta_2: float = 0.999, epsilon: float = 1e-7, rho: float = 0.9, flags: int = 0,
-                 direct_head: bool = False, loss: str = "mse", output_keep=None, cooperative: bool = False):
+                 direct_head: bool = False, loss: str = "mse", output_keep=None, cooperative: bool = False,
+                 precision: str = "bf16"):
         """`direct_head`, `loss` ('mse' | 'mae' | 'huber'), `output_keep` (1/0 per output column) and optimizer
         'AdamTorch' are the pieces of the online-testing MLP (climsim_amd/online_mlp.py); the baseline models leave
         them at their defaults.  `cooperative`: training steps of up to 2048 columns split every 32-row tile over 8 / 4
@@ -90,7 +91,11 @@ class MLPEmulator:
         while such launches run (their workgroups wait for one another; a side-stream kernel or a second process can starve
         them).  Opt-in for that reason: a library cannot know that it owns the device.  A wait that runs out is counted by
         the kernel in host-mapped memory: every later call on the model raises EngineError, `check()` forces the test
-        behind a synchronisation (fit() calls it at the end of every epoch), `coop_timeouts` reads the counter."""
+        behind a synchronisation (fit() calls it at the end of every epoch), `coop_timeouts` reads the counter.
+        `precision`: "bf16" (default: bf16 operands, float32 accumulation, the layer-chain kernels) or "fp32" - the reference's
+        float32 arithmetic (CS_FLAG_FP32: float32 operands on the f32-input MFMA, per-layer kernels, several times the bf16
+        step time); no dropout, no cooperative chain, no grouped launches.  Weights, optimiser state and checkpoints are float32
+        in both modes, so a checkpoint of one precision loads in the other."""
         torch = _torch()
         if not torch.cuda.is_available():
             raise _lib.EngineError("MLPEmulator needs a ROCm GPU (no CPU fallback)")
@@ -100,12 +105,19 @@ class MLPEmulator:
             raise ValueError(f"optimizer must be one of {list(_lib.OPT)}")
         if loss not in _lib.LOSS:
             raise ValueError(f"loss must be one of {list(_lib.LOSS)}")
+        if precision not in ("bf16", "fp32"):
+            raise ValueError(f"precision must be 'bf16' or 'fp32', not {precision!r}")
+        if precision == "fp32" and cooperative:
+            raise ValueError("precision='fp32' runs the per-layer float32 kernels: cooperative=True (the bf16 cooperative chain) does not apply")
+        self.precision = precision
         self.lib = _lib.load()
         self.direct_head, self.loss_name = bool(direct_head), loss
         if self.direct_head:
             flags |= _lib.FLAG_DIRECT_HEAD
         if cooperative:
             flags |= _lib.CS_FLAG_COOP
+        if precision == "fp32":
+            flags |= _lib.CS_FLAG_FP32
         self.cooperative = bool(cooperative)
         self.units = tuple(int(u) for u in units)
         self.activation, self.optimizer_name = activation, optimizer

@@ -68,7 +68,9 @@ class MLP:
     def __init__(self, in_dims: int, out_dims: int, hidden_dims, layers: int, dropout: float = 0.0,
                  output_prune: bool = False, strato_lev_out: int = 15, *, loss: str = "mse", n_relu: int = 8,
                  max_batch: int = 8192, device: Optional[int] = None, seed: Optional[int] = 0, eps: float = 1e-8, flags: int = 0,
-                 dropout_seed: int = 0):
+                 dropout_seed: int = 0, precision: str = "bf16"):
+        """`precision`: "bf16" (default) or "fp32", the reference's float32 arithmetic (MLPEmulator(precision=...)); "fp32"
+        has no dropout."""
         if isinstance(hidden_dims, (list, tuple)):
             assert len(hidden_dims) == layers, "Length of hidden_dims should be equal to layers"      # mlp.py:33
             hidden = [int(h) for h in hidden_dims]
@@ -76,6 +78,8 @@ class MLP:
             hidden = [int(hidden_dims)] * layers
         if not 0.0 <= float(dropout) < 1.0:
             raise ValueError("dropout must be in [0, 1)")
+        if precision == "fp32" and float(dropout) > 0.0:
+            raise ValueError("precision='fp32' has no dropout (the masks are built into the bf16 layer-chain kernels): use dropout=0")
         if output_prune and out_dims < 240 + strato_lev_out:
             raise ValueError("output pruning addresses columns up to 240 + strato_lev_out")
         self.in_dims, self.out_dims, self.hidden_dims, self.layers = in_dims, out_dims, hidden, layers
@@ -84,7 +88,8 @@ class MLP:
         self.engine = MLPEmulator(units=hidden, activation="relu", optimizer="AdamTorch", input_length=in_dims,
                                   output_length_lin=out_dims - n_relu, output_length_relu=n_relu, max_batch=max_batch,
                                   device=device, seed=None, epsilon=eps, flags=flags, direct_head=True, loss=loss,
-                                  output_keep=self.keep if output_prune else None)
+                                  output_keep=self.keep if output_prune else None, precision=precision)
+        self.precision = precision
         self.loss_name = loss
         self.dropout = float(dropout)
         if self.dropout > 0.0:

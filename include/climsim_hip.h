@@ -82,6 +82,16 @@ typedef struct cs_mlp_cfg {
                                     * cs_mlp_check() forces the test behind a stream synchronisation.  The error is sticky. */
 #define CS_FLAG_NO_CHAIN_FB 256    /* forward and backward chain as two launches (default: one launch on 32-row tiles)  */
 #define CS_FLAG_CHAIN_BWD32_ON_FWD64 32   /* tests: 64-row forward tiles (with CHAIN_BM64), 32-row backward tiles    */
+#define CS_FLAG_FP32 1024          /* float32 arithmetic (the reference's: Keras casts its inputs to float32, the online torch MLP is float32):
+                                    * every contraction - forward, data gradients, weight gradients - on float32 operands through gfx950's
+                                    * f32-input MFMA (v_mfma_f32_32x32x2_f32: exact float32 products and sums, no xf32 / TF32 form exists),
+                                    * float32 activations, weights read straight from the float32 master copy (csrc/gemm_f32.h).  Every model
+                                    * shape and head option of the bf16 engine, CS_FLAG_DIRECT_HEAD included; the tile-forcing flags
+                                    * (CHAIN_BM*, GEMM_V1, NO_TR_READ, NO_CHAIN*) are ignored.  Weight gradients without atomics: the same
+                                    * data gives the same bits.  Limits: CS_FLAG_COOP fails cs_mlp_create, cs_mlp_set_dropout(rate > 0)
+                                    * fails, grouped launches refuse such members (cs_mlp_kernel_family: 32, +16 = ELU);
+                                    * cs_mlp_forward_limit = max_batch.  Cost: f32 MFMA runs at 1/16 of the bf16 rate (157 TF peak) -
+                                    * see README for the measured step times. */
 
 /* keras.Model(...) + compile(): allocates weights (zero), optimiser state, workspace. */
 int  cs_mlp_create(cs_mlp_t** out, const cs_mlp_cfg* cfg);
@@ -242,7 +252,7 @@ int cs_metrics_columns_x(const float* pred_dev, const float* target_dev, int64_t
  * gradients, optimisers) whose grids are the members' grids laid end to end.  Members must be of one kernel family
  * (cs_mlp_kernel_family: 1 = hidden widths 128/256/512 and 128 outputs, 2 = any widths up to 1024; +16 = ELU) on one
  * device; they need not share an architecture.  Results per member are those of cs_mlp_train_step on that member alone
- * (same kernels bodies, same arithmetic). */
+ * (same kernels bodies, same arithmetic).  CS_FLAG_FP32 models are family 32 (+16 = ELU) and cannot be grouped. */
 typedef struct cs_mlp_group cs_mlp_group_t;
 #define CS_GROUP_MAX_MEMBERS 32
 int cs_mlp_kernel_family(const cs_mlp_t* h);

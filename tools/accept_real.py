@@ -144,7 +144,8 @@ def train_and_score(args):
     if args.model == "mlp":
         from climsim_amd.mlp import CyclicalLearningRate, MLPEmulator
         epochs = args.epochs or 30
-        m = MLPEmulator(units=(768, 640, 512, 640, 640), activation="leakyrelu", optimizer="RAdam", max_batch=3072, seed=args.seed)
+        m = MLPEmulator(units=(768, 640, 512, 640, 640), activation="leakyrelu", optimizer="RAdam", max_batch=3072, seed=args.seed,
+                        precision=getattr(args, "precision", "bf16"))
         hist = m.fit(xt_d, yt_d, batch_size=3072, epochs=epochs, validation_data=(xv_d, yv_d),
                      learning_rate=CyclicalLearningRate(2.5e-4, 2.5e-3, step_size=2 * (26280 // 3072)), seed=args.seed,
                      checkpoint_best=best, early_stopping_patience=8, csv_log=os.path.join(args.out, "accept_mlp_log.csv"), verbose=1)
@@ -173,6 +174,8 @@ def main(argv=None):
     ap.add_argument("--out", default="accept_out")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--tolerance", type=float, default=0.01, help="relative MAE tolerance of the verdict (1 %%)")
+    ap.add_argument("--precision", choices=("bf16", "fp32"), default="bf16",
+                    help="MLP arithmetic: bf16 operands (default) or the reference's float32 (CS_FLAG_FP32)")
     ap.add_argument("--limit-rows", type=int, default=0, help="development: use only the first N rows of every split")
     args = ap.parse_args(argv)
     df_var, hist = train_and_score(args)
@@ -181,7 +184,7 @@ def main(argv=None):
     print(format_table(rows, args.model))
     print(f"verdict: {'PASS' if v['passed'] else 'FAIL'} - worst MAE difference {100 * (v['worst_rel_diff'] or float('nan')):.2f} % ({v['worst_variable']}), bar {100 * v['tolerance']:.1f} %")
     with open(os.path.join(args.out, f"accept_{args.model}.json"), "w") as f:
-        json.dump({"model": args.model, "rows": rows, "verdict": v, "history": {k: [float(x) for x in vals] for k, vals in hist.items()}}, f, indent=1)
+        json.dump({"model": args.model, "precision": args.precision, "rows": rows, "verdict": v, "history": {k: [float(x) for x in vals] for k, vals in hist.items()}}, f, indent=1)
     return 0 if v["passed"] else 1
 
 
